@@ -13,19 +13,28 @@ Workload (one "step" = one pass of the hot path over one batch):
   rather than from the 256 MB Infinity Cache. Per-rank work is fixed as N
   grows (weak scaling); no data-path collective: segments are independent.
 
-Also reported (N=1, rank 0): F9000 (configs[2]) and ZIPF (configs[3]) rates,
-the plain streaming-read ceiling on the same buffer, the end-to-end host path
-(pinned H2D + kernel + D2H), and the reference CPU checksum timed on this
-box's cores (cpu_baseline).
+A plain run does only that: data, warm-up, the K timed steps, the result line
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+With --full, also reported: parity of the timed outputs, repeated replays, the
+serial-chain roofline, the host-start leg, the N>1 exchange legs and (N=1,
+rank 0) F9000 (configs[2]) and ZIPF (configs[3]) rates, the plain
+streaming-read ceiling on the same buffer, the end-to-end host path (pinned
+H2D + kernel + D2H), and the reference CPU checksum timed on the host's cores
+(cpu_baseline).
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
+                       [--dump-outputs DIR]
+       --dump-outputs DIR writes the timed steps' results as DIR/<name>.npy.
+       --no-extras, --no-cpu-baseline and --cpu-seconds trim a --full run;
+       without --full there is nothing for them to trim and they do nothing.
        N>1 runs one rank per GPU: under `python -m torch.distributed.run
        --nproc-per-node N ...`, or, with no launcher (WORLD_SIZE unset), this
        script starts that launcher itself as a child process (before any GPU
        call), relays its output and exits with its status.
 
-Parity of the measured work: the result buffers are poisoned (0xA5 bytes)
-before every timed replay and the digests of what the replay wrote are
+Parity of the measured work (--full): the result buffers are poisoned (0xA5
+bytes) before every timed replay and the digests of what the replay wrote are
 compared with the reference's afterwards (per batch, tests/golden).
 """
 from __future__ import annotations
@@ -55,9 +64,22 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=1024)
     p.add_argument("--warmup", type=int, default=32)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything beside the headline: "
+                        "parity of the timed outputs against the reference digests, the "
+                        "repeated and ungated replays, the serial-chain roofline, the "
+                        "host-start leg, the N>1 exchange legs, the side measurements "
+                        "(extras) and the CPU baseline. Without it the run sets up, warms "
+                        "up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what they computed as DIR/<name>.npy "
+                        "(float32): checksums = the last timed step's 65,536 results, "
+                        "checksums_timed = every result word of the timed steps, one row "
+                        "per batch of the shard (N>1: <name>_rank<r>.npy per rank)")
     p.add_argument("--no-extras", action="store_true",
-                   help="skip F9000/ZIPF/e2e/ceiling side measurements")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+                   help="with --full: skip F9000/ZIPF/e2e/ceiling side measurements")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="with --full: skip the CPU baseline")
     p.add_argument("--cpu-seconds", type=float, default=1.5,
                    help="wall seconds per CPU-baseline leg")
     p.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
@@ -454,20 +476,31 @@ def main():
     value = total_bytes / t_max / GIB
     per_launch_s = t_local / steps_done
 
+    if args.dump_outputs:
+        progress("dump outputs")
+        dump_outputs(args.dump_outputs, outs, (steps_done - 1) % NBATCH, rank, world)
+
+    # everything below the timed steps that is not the headline runs under
+    # --full only; a plain run goes straight to its result line
+    full = args.full
+
     # ---- parity of what the timed replay wrote: per-batch digests vs the
     # reference's (shard <rank> of M8x1500, batch b = steps i with i % 16 == b)
-    gold = golden_digests().get("M8x1500", {})
     written = sorted({i % NBATCH for i in range(steps_done)})
-    got_b = row_digests(outs, NBATCH, NSEG)
-    ok = False
-    if rank < 8 and gold.get("shards") and "batches" in gold["shards"][rank]:
-        want_b = gold["shards"][rank]["batches"]
-        ok = all(got_b[b] == want_b[b] for b in written)
-    parity = "ok" if all_ranks_ok(ok, dist, cdev) else "MISMATCH"
-    parity_checked = (f"result words poisoned (0xA5A5) before the timed replay; the "
-                      f"{len(written)} batches it wrote per rank checked against the "
-                      "reference's per-batch digests of M8x1500 shard <rank>")
-    if len(written) < NBATCH:
+    parity = "not checked (plain run: --full compares the timed outputs with the reference)"
+    parity_checked = None
+    if full:
+        gold = golden_digests().get("M8x1500", {})
+        got_b = row_digests(outs, NBATCH, NSEG)
+        ok = False
+        if rank < 8 and gold.get("shards") and "batches" in gold["shards"][rank]:
+            want_b = gold["shards"][rank]["batches"]
+            ok = all(got_b[b] == want_b[b] for b in written)
+        parity = "ok" if all_ranks_ok(ok, dist, cdev) else "MISMATCH"
+        parity_checked = (f"result words poisoned (0xA5A5) before the timed replay; the "
+                          f"{len(written)} batches it wrote per rank checked against the "
+                          "reference's per-batch digests of M8x1500 shard <rank>")
+    if full and len(written) < NBATCH:
         # the later legs use the whole shard's results
         for b in range(NBATCH):
             step(b)
@@ -477,7 +510,7 @@ def main():
     # the replay stream, max over ranks): the spread of `value` within one
     # session (make the headline reproducible)
     replays = []
-    if graph is not None:
+    if full and graph is not None:
         for _ in range(7):
             if world > 1:
                 dist.barrier()
@@ -493,7 +526,7 @@ def main():
     # as soon as it is queued, so the host's submission of the graph counts,
     # as it did in the rounds before the gate
     ungated = []
-    if graph is not None:
+    if full and graph is not None:
         for _ in range(3):
             if world > 1:
                 dist.barrier()
@@ -505,14 +538,16 @@ def main():
             tr = max_over_ranks(ev0.elapsed_time(ev1) / 1e3, dist, cdev)
             ungated.append(total_bytes / tr / GIB)
 
-    digest = fnv1a_u16(outs.cpu().numpy().view(np.uint16))
-    shard_digests = gather_strings(digest, dist)
+    shard_digests = None
+    if full:
+        digest = fnv1a_u16(outs.cpu().numpy().view(np.uint16))
+        shard_digests = gather_strings(digest, dist)
 
     # the kernel alone, as one serial chain of the same launches (the figure
     # rocprofv3 --stats averages), measured after the timed region so that
     # nothing but the warm replay precedes it
     serial_s = None
-    if graph is not None and args.streams > 1:
+    if full and graph is not None and args.streams > 1:
         def serial(i, st):
             b = i % NBATCH
             fixed(base + b * batch_bytes, SEG, SEG, None, None, None,
@@ -525,7 +560,7 @@ def main():
     # data starting on GPU 0 scattered over xGMI
     exchange = None
     multi = None
-    if world > 1:
+    if full and world > 1:
         exchange = exchange_sequential(torch, dist, cdev, outs, total_bytes, t_max,
                                        shard_digests, rank, world)
         multi = multi_rank_legs(torch, dist, csum, dev, cdev, stream, arena, outs,
@@ -533,7 +568,9 @@ def main():
 
     # the same shards starting in host memory, every rank over its own PCIe
     # link (§8e; beside `value`, never as it)
-    host_start = _leg(host_start_leg, torch, dist, csum, cdev, arena, rank, world)
+    host_start = None
+    if full:
+        host_start = _leg(host_start_leg, torch, dist, csum, cdev, arena, rank, world)
 
     result = {
         "metric": METRIC,
@@ -543,8 +580,12 @@ def main():
                       "at a time is roofline.avg_launch_us / roofline.frac",
         "unit": "GiB/s",
         "n_gpus": dist.get_world_size() if dist.is_initialized() else 1,
+        "full": full,
         "steps": steps_done,
         "warmup": args.warmup,
+        "warmup_run": f"{max(args.warmup, NBATCH)} eager steps (at least one per batch of "
+                      "the shard)" + ("" if graph is None else
+                                      f", then one untimed replay of the {steps_done}-step graph"),
         "ms_per_step": round(t_max / steps_done * 1e3, 5),
         "higher_is_better": True,
         "scaling": "weak",
@@ -593,18 +634,15 @@ def main():
     # rocprofv3 --stats averages). With several graph branches the timed
     # region's per-launch time is shorter than any one dispatch (launches
     # overlap), so it is reported separately as "pipeline".
-    serial_s = per_launch_s if serial_s is None else serial_s
-    achieved = batch_bytes / serial_s / 1e9
+    # A plain run has no serial chain of its own: it reports the pipeline
+    # figure of its timed steps alone (--full adds achieved / frac).
     result["roofline"] = {
         "bound": "hbm",
-        "achieved": round(achieved, 1),
         "peak": HBM_PEAK_GBS,
         "unit": "GB/s",
-        "frac": round(achieved / HBM_PEAK_GBS, 4),
         "traffic": read_traffic("F1500"),
         "kernel": f"csum_kernel<G={tun.group},U={tun.unroll},FixedSegs>",
         "bytes_per_launch": batch_bytes,
-        "avg_launch_us": round(serial_s * 1e6, 3),
         "pipeline": {
             "branches": args.streams if graph is not None else 1,
             "us_per_launch": round(per_launch_s * 1e6, 3),
@@ -612,12 +650,20 @@ def main():
             "frac": round(batch_bytes / per_launch_s / 1e9 / HBM_PEAK_GBS, 4),
         },
     }
+    if full:
+        serial_s = per_launch_s if serial_s is None else serial_s
+        achieved = batch_bytes / serial_s / 1e9
+        result["roofline"].update({
+            "achieved": round(achieved, 1),
+            "frac": round(achieved / HBM_PEAK_GBS, 4),
+            "avg_launch_us": round(serial_s * 1e6, 3),
+        })
 
-    if world == 1 and rank == 0 and not args.no_extras:
+    if full and world == 1 and rank == 0 and not args.no_extras:
         progress("extras (child process)")
         result["extras"] = extras_in_child()
 
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         progress("cpu baseline")
         result["cpu_baseline"] = cpu_baseline(arena, batch_bytes, args.cpu_seconds)
 
@@ -631,6 +677,22 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         print(json.dumps(result), flush=True)
+
+
+def dump_outputs(path, outs, last_batch, rank, world):
+    """--dump-outputs DIR: the timed steps' results as float32 .npy files (a
+    u16 checksum is exact in float32; 4.25 MB per rank in all). `checksums` is
+    what the last timed step returned to its caller, the 65,536 checksums of
+    batch `last_batch`; `checksums_timed` is the whole result buffer, one row
+    per batch of the shard, as the timed steps left it (every word was set to
+    0xA5A5 before them, so a row no timed step wrote, with fewer than 16
+    steps, holds 42405.0). The data is the seeded SplitMix64 stream, so two
+    runs with the same arguments write the same files."""
+    os.makedirs(path, exist_ok=True)
+    o = outs.cpu().numpy().view(np.uint16).reshape(NBATCH, NSEG).astype(np.float32)
+    tag = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(path, f"checksums{tag}.npy"), o[last_batch])
+    np.save(os.path.join(path, f"checksums_timed{tag}.npy"), o)
 
 
 def summary_of(result):

@@ -1,5 +1,5 @@
 #!/bin/bash
-# TEST INFRASTRUCTURE (integration/Makefile, target `dropin`): removes the
+# TEST INFRASTRUCTURE (oracle/integration.mk, target `dropin`): removes the
 # reference's own checksum definitions from its compiled objects, so that a
 # stack linked from them takes every checksum from libtulips_csum.so. No
 # reference source is edited; only the objects built from it are.

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE — the drop-in proven at the reference's own call sites.
 //
-// This program is linked (integration/Makefile, target `dropin`) against
+// This program is linked (oracle/integration.mk, target `dropin`) against
 //   1. tulips_amd/libtulips_csum.so (the product), FIRST in link order, and
 //   2. a build of the reference's unmodified src/stack + src/system + src/api
 //      + src/transport/list sources whose own definitions of the checksum

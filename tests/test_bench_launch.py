@@ -6,8 +6,10 @@ prints the one JSON line.
 
 The CPU test drives that launch path with --dry-run (the ranks form the gloo
 group and report it, no GPU call); the GPU test runs the whole bench with 4
-ranks sharing the one GPU of the test box (--one-device, gloo), every rank's
-measured shard checked against the reference's digests.
+ranks sharing the one GPU of the test host (--one-device, gloo, --full), every
+rank's measured shard checked against the reference's digests. A plain
+one-GPU run is checked for what it leaves out and for what --dump-outputs
+writes.
 """
 import json
 import os
@@ -61,7 +63,7 @@ def test_single_rank_dry_run_and_world_mismatch():
 def test_self_launched_four_ranks_on_one_gpu():
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "4",
                         "--dist-backend", "gloo", "--one-device", "--steps", "32",
-                        "--warmup", "4", "--no-extras"],
+                        "--warmup", "4", "--full", "--no-extras"],
                        capture_output=True, text=True, env=_env(), timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
@@ -79,9 +81,48 @@ def test_self_launched_four_ranks_on_one_gpu():
     hs = line["host_start"]
     assert hs["parity"] == "ok", hs
     assert hs["aggregate_GiBps"] > 0 and hs["bytes_per_rank"] == 16 * 65536 * 1500
-    # the summary is the line's last key (the driver keeps the output's tail)
+    # the summary is the line's last key (a reader of the output's tail sees it)
     assert list(line)[-1] == "summary"
     assert line["summary"]["host_start_GiBps"] == hs["aggregate_GiBps"]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_what_it_timed(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` times K steps and prints the
+    line with nothing that belongs to --full; --dump-outputs writes the timed
+    steps' results as float32 .npy, and those are the reference's checksums
+    (tests/golden: M8x1500 shard 0, batch b written by steps i % 16 == b)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    steps = 20
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1",
+                        "--steps", str(steps), "--warmup", "5", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, env=_env(), timeout=280, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = _json_lines(r.stdout)
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = lines[0]
+    assert line["metric"] == bench.METRIC and line["unit"] == "GiB/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "u16"
+    assert line["steps"] == steps and line["full"] is False
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    # value and ms_per_step describe the same timed steps (both are rounded)
+    gib = bench.NSEG * bench.SEG / bench.GIB
+    assert line["value"] == pytest.approx(gib / (line["ms_per_step"] / 1e3), rel=1e-3)
+    for key in ("extras", "cpu_baseline", "value_replays", "value_replays_ungated"):
+        assert key not in line
+    assert line["host_start"] is None and "frac" not in line["roofline"]
+    assert sorted(os.listdir(out)) == ["checksums.npy", "checksums_timed.npy"]
+    last = np.load(out / "checksums.npy")
+    timed = np.load(out / "checksums_timed.npy")
+    assert last.dtype == np.float32 and last.shape == (bench.NSEG,)
+    assert timed.dtype == np.float32 and timed.shape == (bench.NBATCH, bench.NSEG)
+    assert np.array_equal(last, timed[(steps - 1) % bench.NBATCH])
+    want = bench.golden_digests()["M8x1500"]["shards"][0]["batches"]
+    got = [bench.fnv1a_u16(timed[b].astype(np.uint16)) for b in range(bench.NBATCH)]
+    assert got == want
 
 
 def test_summary_of_picks_the_judged_figures():

@@ -1,6 +1,7 @@
 """The drop-in at the reference's own call sites.
 
-integration/Makefile (target `dropin`) compiles the reference's unmodified
+oracle/integration.mk (target `dropin`, built by build() into
+oracle/_ref/integration/dropin/) compiles the reference's unmodified
 src/stack + src/system + src/api + src/transport/list sources three times —
 the gate variants of CMakeLists.txt:46-47,151-163:
 
@@ -28,7 +29,7 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BUILD = os.path.join(ROOT, "integration", "_build", "dropin")
+BUILD = os.path.join(ROOT, "oracle", "_ref", "integration", "dropin")
 SYMS = {
     "utils::checksum": "_ZN6tulips5stack5utils8checksumEtPKht",
     "ipv4::checksum": "_ZN6tulips5stack4ipv48checksumEPKh",
@@ -43,7 +44,8 @@ def harness(variant):
 
 
 needs_build = pytest.mark.skipif(not os.path.exists(harness("default")),
-                                 reason="integration/_build/dropin not built (no reference tree)")
+                                 reason="oracle/_ref/integration/dropin not built "
+                                        "(no reference tree)")
 
 
 def run(variant, *args, env=None, timeout=120):

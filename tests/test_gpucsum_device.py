@@ -1,7 +1,7 @@
 """transport::gpucsum::Device — the batched receive-validation decorator
 (integration/include/tulips/transport/gpucsum/Device.h).
 
-integration/_build/libgpucsum_test.so (integration/Makefile) is the decorator
+oracle/_ref/integration/libgpucsum_test.so (oracle/integration.mk) is the decorator
 compiled against the reference's headers, wrapping the reference's own
 list::Device (src/transport/list/Device.cpp). The frames of
 tests/golden/frames.npz are committed on a peer list device, polled through
@@ -17,13 +17,13 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "integration", "_build", "libgpucsum_test.so")
+HARNESS = os.path.join(ROOT, "oracle", "_ref", "integration", "libgpucsum_test.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "frames.npz")
 
 VALIDATE_IP_CSUM, VALIDATE_L4_CSUM = 0x1, 0x2   # include/tulips/transport/Device.h:29-30
 
 needs_harness = pytest.mark.skipif(not os.path.exists(HARNESS),
-                                   reason="integration/_build not built (no reference tree)")
+                                   reason="oracle/_ref/integration not built (no reference tree)")
 
 
 def harness():

@@ -25,10 +25,11 @@ rocminfo 2>/dev/null | grep -m1 -E "gfx9" || true
 if [ -z "${PROF_ONLY:-}" ]; then   # PROF_ONLY=1: the rocprofv3 steps alone
 step pytest_gpu 600 python -u -m pytest tests -q -m gpu -x -p no:cacheprovider --timeout 300 --timeout-method thread
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 400 python bench.py
+step bench 400 python bench.py --full
 tail -1 $OUT/bench.log > $OUT/bench.json
-# the driver's form (python3 bench.py --gpus 1 --steps 20 --warmup 5)
-step bench_driver 400 python bench.py --gpus 1 --steps 20 --warmup 5
+# the short form (--gpus 1 --steps 20 --warmup 5) with every side
+# measurement; without --full it prints the headline alone
+step bench_driver 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full
 tail -1 $OUT/bench_driver.log > $OUT/bench_driver.json
 fi
 # bench.py runs its side measurements in a child process, which rocprofv3
@@ -36,11 +37,11 @@ fi
 # (--extras-child) are profiled as two programs and their CSVs merged; the
 # aligned-stride legs are left out of those passes (same kernels and grids as
 # the rotated F1500 / F9000 batches, so their counters would mix)
-step stats 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_h -o run -- python bench.py --no-cpu-baseline --no-extras
+step stats 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_h -o run -- python bench.py --full --no-cpu-baseline --no-extras
 BENCH_EXTRAS_SKIP=aligned_strides step stats_x 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_x -o run -- python bench.py --extras-child
-step pmc_fetch 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_h -o run -- python bench.py --no-cpu-baseline --no-extras --steps 64 --warmup 16
+step pmc_fetch 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_h -o run -- python bench.py --full --no-cpu-baseline --no-extras --steps 64 --warmup 16
 BENCH_EXTRAS_SKIP=aligned_strides step pmc_fetch_x 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_x -o run -- python bench.py --extras-child
-step pmc_write 240 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_h -o run -- python bench.py --no-cpu-baseline --no-extras --steps 64 --warmup 16
+step pmc_write 240 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_h -o run -- python bench.py --full --no-cpu-baseline --no-extras --steps 64 --warmup 16
 BENCH_EXTRAS_SKIP=aligned_strides step pmc_write_x 240 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_x -o run -- python bench.py --extras-child
 python tools/merge_csv.py $OUT/stats/run_kernel_trace.csv $OUT/stats_h/run_kernel_trace.csv $OUT/stats_x/run_kernel_trace.csv
 python tools/merge_csv.py $OUT/stats/run_kernel_stats.csv $OUT/stats_h/run_kernel_stats.csv $OUT/stats_x/run_kernel_stats.csv
@@ -57,6 +58,6 @@ rm -f $OUT/stats/run_kernel_trace.csv $OUT/pmc_fetch/run_counter_collection.csv 
 # (no launcher: bench.py starts torch.distributed.run itself, as under the
 # driver's `python bench.py --gpus 8`)
 [ -n "${PROF_ONLY:-}" ] && { echo "== done (profiles only)"; exit 0; }
-step rehearsal_w8 600 python bench.py --gpus 8 --dist-backend gloo --one-device --steps 64 --warmup 16 --no-cpu-baseline
+step rehearsal_w8 600 python bench.py --gpus 8 --dist-backend gloo --one-device --steps 64 --warmup 16 --full --no-cpu-baseline
 tail -1 $OUT/rehearsal_w8.log > $OUT/rehearsal_w8.json
 echo "== done"
