@@ -31,6 +31,9 @@
  *                             src/stack/ipv4/Producer.cpp:81 generate), done
  *                             for a whole batch of device-resident segments by
  *                             HIP kernels on gfx950.
+ *   tulips_csum_batch_sg      the same for segments held as several fragments
+ *                             (the header and payload ranges of src/transport/
+ *                             ofed/Device.cpp:720-725), summed where they lie.
  *   tulips_csum_batch_host    the same for host-resident segments (pinned
  *                             staging, H2D, kernel, D2H), the path a transport
  *                             poll burst would take (src/transport/ofed/
@@ -141,6 +144,69 @@ int tulips_csum_verify_arena(const uint8_t* base, uint64_t arena_bytes,
                              const uint32_t* src, const uint32_t* dst, uint16_t* out,
                              uint32_t* bad_count, uint32_t n, uint32_t mode,
                              void* stream);
+
+/* ---- scatter-gather batches ---------------------------------------------- */
+/*
+ * Segments made of fragments: a header ring plus registered application
+ * memory (zero-copy send, as the reference posts TSO with a header and a
+ * separate payload range, src/transport/ofed/Device.cpp:720-725), NIC
+ * header-data split on receive, a reassembly queue of out-of-order pieces.
+ *
+ * Fragment j is base[frag_offsets[j] .. frag_offsets[j] + frag_lengths[j]):
+ * any byte alignment, length 0 allowed, fragments may overlap or alias.
+ * Segment i is the concatenation, in order, of fragments seg_first[i] ..
+ * seg_first[i+1] - 1: seg_first has n + 1 entries, is non-decreasing,
+ * seg_first[0] == 0 and seg_first[n] == nfrags; a segment may have no
+ * fragment; its total length is at most 65535.
+ *
+ * out[i] is exactly what tulips_csum_batch returns for a contiguous copy of
+ * segment i's bytes, under the same mode / seeds / src / dst /
+ * TULIPS_CSUM_COMPLEMENT rules (TCP: `len` is the segment's total). It is
+ * NOT the reference call chained fragment by fragment: an odd-length
+ * fragment moves every later byte to the other byte lane (fragments {0x01}
+ * and {0x02} give RAW 0x0102, not 0x0300). An empty segment gives its seed
+ * (RAW). All arrays are device pointers; with nfrags == 0 base, frag_offsets
+ * and frag_lengths may be NULL. n == 0 is a no-op returning OK. Stateless:
+ * no per-stream state, capturable as it stands.
+ *
+ * A plan that breaks the rules above (or a segment longer than 65535) gets
+ * unspecified results for its segments; seg_first is still read only in
+ * [0, n], the fragment arrays only in [0, nfrags), and data only inside the
+ * 16-byte-aligned hull of a fragment that some segment names.
+ */
+int tulips_csum_batch_sg(const uint8_t* base, const uint64_t* frag_offsets,
+                         const uint16_t* frag_lengths, uint32_t nfrags,
+                         const uint32_t* seg_first, const uint16_t* seeds,
+                         const uint32_t* src, const uint32_t* dst, uint16_t* out,
+                         uint32_t n, uint32_t mode, void* stream);
+
+/*
+ * tulips_csum_verify for scatter-gather segments (mode INET or TCP):
+ * *bad_count (device uint32) is overwritten with the number of segments in
+ * [0, n) whose result is not 0xffff (0 for n == 0); `out` may be NULL when
+ * only the count is wanted. Unlike tulips_csum_verify it keeps no
+ * per-stream state (the count is zeroed on `stream`, then each wave adds
+ * its total with one atomic), so a captured call owns nothing.
+ */
+int tulips_csum_verify_sg(const uint8_t* base, const uint64_t* frag_offsets,
+                          const uint16_t* frag_lengths, uint32_t nfrags,
+                          const uint32_t* seg_first, const uint32_t* src,
+                          const uint32_t* dst, uint16_t* out, uint32_t* bad_count,
+                          uint32_t n, uint32_t mode, void* stream);
+
+/*
+ * The same batch on host arrays, computed on the calling thread (no GPU
+ * involved): the role tulips_csum_validate_frames_cpu plays for frames.
+ * `out` (n entries) and `bad_count` (one uint32: results that are not
+ * 0xffff, or not 0 with TULIPS_CSUM_COMPLEMENT) may each be NULL, not both.
+ * The plan is checked first: InvalidArgument unless seg_first is
+ * non-decreasing and seg_first[n] <= nfrags.
+ */
+int tulips_csum_batch_sg_cpu(const uint8_t* base, const uint64_t* frag_offsets,
+                             const uint16_t* frag_lengths, uint32_t nfrags,
+                             const uint32_t* seg_first, const uint16_t* seeds,
+                             const uint32_t* src, const uint32_t* dst, uint16_t* out,
+                             uint32_t* bad_count, uint32_t n, uint32_t mode);
 
 /* ---- host-resident batches (end-to-end path) ----------------------------- */
 
@@ -598,6 +664,18 @@ int tulips_csum_batch_arena_tuned(const uint8_t* base, uint64_t arena_bytes,
                                   const uint32_t* dst, uint16_t* out, uint32_t n,
                                   uint32_t mode, const tulips_csum_tuning* tuning,
                                   void* stream);
+
+/* tulips_csum_batch_sg with an explicit geometry: one wave per
+ * tuning->group segments, tuning->unroll 64-chunk windows per
+ * double-buffered batch (group x unroll 8x2, 8x4, 16x2, 16x4; 0 = the
+ * default 8x4), nontemporal (bit 0: nt loads, -1 = on), block (256, 512 or
+ * 1024 threads; 0 = 256); kind, max_blocks and sps are ignored. */
+int tulips_csum_batch_sg_tuned(const uint8_t* base, const uint64_t* frag_offsets,
+                               const uint16_t* frag_lengths, uint32_t nfrags,
+                               const uint32_t* seg_first, const uint16_t* seeds,
+                               const uint32_t* src, const uint32_t* dst, uint16_t* out,
+                               uint32_t n, uint32_t mode,
+                               const tulips_csum_tuning* tuning, void* stream);
 
 /* Frame kernels (include/tulips_csum.h) with an explicit geometry: op 0 =
  * tulips_csum_validate_frames, op 1 = tulips_csum_generate_frames (counters

@@ -476,6 +476,12 @@ counted(void* stream, uint32_t* count, const F& launch)
 
 } // namespace
 
+int
+tulips_amd::status_of_hip(hipError_t e)
+{
+  return status_of(e);
+}
+
 extern "C" {
 
 int

@@ -54,6 +54,10 @@ constexpr uint32_t CNT_SHARDS = 32, CNT_LINE = 32;
 hipError_t launch_counters_finalize(uint32_t* shards, uint32_t* out, uint32_t nout,
                                     hipStream_t stream);
 
+// csum_capi.hip: the tulips::Status of a HIP error; a failure's text is kept
+// for tulips_csum_last_error.
+int status_of_hip(hipError_t e);
+
 hipError_t launch_fixed(const uint8_t* base, uint64_t stride, uint32_t len,
                         const LaunchArgs& a, hipStream_t stream);
 hipError_t launch_var(const uint8_t* base, const uint64_t* offs,

@@ -173,6 +173,15 @@ _SIGNATURES = {
                                                               _vp, C.c_uint32, _vp, _vp, _vp,
                                                               _vp]),
     "tulips_csum_mctx_set_peer_mode": (C.c_int, [_vp, C.c_int]),
+    "tulips_csum_batch_sg": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                       C.c_uint32, C.c_uint32, _vp]),
+    "tulips_csum_batch_sg_tuned": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp,
+                                             _vp, C.c_uint32, C.c_uint32,
+                                             C.POINTER(Tuning), _vp]),
+    "tulips_csum_verify_sg": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp, _vp,
+                                        C.c_uint32, C.c_uint32, _vp]),
+    "tulips_csum_batch_sg_cpu": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, C.c_uint32, C.c_uint32]),
 }
 
 # include/tulips_csum.h TULIPS_FRAME_* (per-frame validation flags)
@@ -397,6 +406,90 @@ def verify(arena, offsets, lengths, *, src=None, dst=None, mode: int = TCP,
                                 n, mode, _stream(stream))
     _check(rc, "tulips_csum_verify")
     return bad
+
+
+# The shipped scatter-gather geometries (tulips_csum_batch_sg_tuned): segments
+# per wave x 64-chunk windows per batch.
+SG_GEOMETRIES = ((8, 2), (8, 4), (16, 2), (16, 4))
+
+
+def _sg_sizes(frag_offsets, frag_lengths, seg_first):
+    nfrags = int(frag_offsets.numel())
+    if int(frag_lengths.numel()) != nfrags:
+        raise ValueError("frag_offsets/frag_lengths size mismatch")
+    if int(seg_first.numel()) < 1:
+        raise ValueError("seg_first holds n + 1 entries")
+    return nfrags, int(seg_first.numel()) - 1
+
+
+def batch_sg(arena, frag_offsets, frag_lengths, seg_first, *, seeds=None, src=None,
+             dst=None, mode: int = RAW, out=None, stream=None,
+             tuning: Tuning | None = None):
+    """Checksum scatter-gather segments (tulips_csum_batch_sg): fragment j =
+    arena[frag_offsets[j] : frag_offsets[j] + frag_lengths[j]], segment i =
+    the concatenation of fragments seg_first[i] .. seg_first[i+1] - 1.
+
+    arena: uint8 device tensor; frag_offsets: uint64/int64; frag_lengths:
+    uint16; seg_first: uint32/int32 with n + 1 entries; seeds/src/dst as
+    batch(). Returns the uint16 result tensor (enqueued on `stream`).
+    """
+    nfrags, n = _sg_sizes(frag_offsets, frag_lengths, seg_first)
+    _check_sizes(n, seeds=seeds, src=src, dst=dst, out=out)
+    if out is None:
+        out = _alloc_out(n, seg_first)
+    args = (_addr(arena), _addr(frag_offsets), _addr(frag_lengths), nfrags, _addr(seg_first),
+            _addr(seeds), _addr(src), _addr(dst), _addr(out), n, mode)
+    if tuning is None:
+        rc = lib.tulips_csum_batch_sg(*args, _stream(stream))
+    else:
+        rc = lib.tulips_csum_batch_sg_tuned(*args, C.byref(tuning), _stream(stream))
+    _check(rc, "tulips_csum_batch_sg")
+    return out
+
+
+def verify_sg(arena, frag_offsets, frag_lengths, seg_first, *, src=None, dst=None,
+              mode: int = TCP, out=None, bad=None, stream=None):
+    """Count scatter-gather segments whose INET/TCP result is not 0xffff;
+    returns the uint32 device counter (and fills `out` when given)."""
+    import torch
+    nfrags, n = _sg_sizes(frag_offsets, frag_lengths, seg_first)
+    _check_sizes(n, src=src, dst=dst, out=out)
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int32, device=seg_first.device)
+    rc = lib.tulips_csum_verify_sg(_addr(arena), _addr(frag_offsets), _addr(frag_lengths),
+                                   nfrags, _addr(seg_first), _addr(src), _addr(dst),
+                                   _addr(out), _addr(bad), n, mode, _stream(stream))
+    _check(rc, "tulips_csum_verify_sg")
+    return bad
+
+
+def batch_sg_cpu(arena, frag_offsets, frag_lengths, seg_first, *, seeds=None, src=None,
+                 dst=None, mode: int = RAW, with_bad: bool = False):
+    """batch_sg on host arrays, computed on this thread by the library's host
+    code (tulips_csum_batch_sg_cpu; no GPU). Returns the uint16 results, with
+    the count of results that do not verify when `with_bad`."""
+    import numpy as np
+    ar = _host(arena, np.uint8)
+    off = _host(frag_offsets, np.uint64)
+    ln = _host(frag_lengths, np.uint16)
+    first = _host(seg_first, np.uint32)
+    nfrags = len(off.keep)
+    if len(ln.keep) != nfrags:
+        raise ValueError("frag_offsets/frag_lengths size mismatch")
+    if len(first.keep) < 1:
+        raise ValueError("seg_first holds n + 1 entries")
+    n = len(first.keep) - 1
+    sd, sr, ds = _host(seeds, np.uint16), _host(src, np.uint32), _host(dst, np.uint32)
+    for name, a in (("seeds", sd), ("src", sr), ("dst", ds)):
+        if a.keep is not None and len(a.keep) < n:
+            raise ValueError(f"{name} holds {len(a.keep)} entries, batch has {n}")
+    out = np.empty(max(n, 1), dtype=np.uint16)
+    bad = np.zeros(1, dtype=np.uint32)
+    _check(lib.tulips_csum_batch_sg_cpu(ar.ptr, off.ptr, ln.ptr, nfrags, first.ptr, sd.ptr,
+                                        sr.ptr, ds.ptr, out.ctypes.data, bad.ctypes.data, n,
+                                        mode),
+           "tulips_csum_batch_sg_cpu")
+    return (out[:n], int(bad[0])) if with_bad else out[:n]
 
 
 def default_tuning(fixed_length: int = 0, variable: bool = False) -> Tuning:
