@@ -200,7 +200,8 @@ int tulips_csum_verify_sg(const uint8_t* base, const uint64_t* frag_offsets,
  * `out` (n entries) and `bad_count` (one uint32: results that are not
  * 0xffff, or not 0 with TULIPS_CSUM_COMPLEMENT) may each be NULL, not both.
  * The plan is checked first: InvalidArgument unless seg_first is
- * non-decreasing and seg_first[n] <= nfrags.
+ * non-decreasing and seg_first[n] <= nfrags. A rejected call writes nothing,
+ * neither `out` nor `bad_count`.
  */
 int tulips_csum_batch_sg_cpu(const uint8_t* base, const uint64_t* frag_offsets,
                              const uint16_t* frag_lengths, uint32_t nfrags,
@@ -454,9 +455,16 @@ int tulips_csum_generate_fields(const uint8_t* base, const uint64_t* offsets,
  * out_first[i+1] - 1, out_first[n] is the total. Segment j is written to
  * out_base + j * out_stride (out_base 16-byte aligned, out_stride a multiple
  * of 16) with its length in out_lengths[j]; a segment longer than out_stride
- * is not written (length 0), nor is any j >= out_capacity. With
- * out_capacity == 0 only out_first is computed (to size the output).
+ * is not written (length 0, its slot untouched), nor is any j >= out_capacity
+ * (neither its slot nor out_lengths[j]). With out_capacity == 0 only
+ * out_first is computed (to size the output).
  * n <= 2^24, 1 <= mss <= 65535. Input frames are not modified.
+ *
+ * The slot tail: a segment of L bytes is stored as whole 16-byte chunks, so
+ * slot bytes [L, round_up(L, 16)) are written as zeros and slot bytes
+ * [round_up(L, 16), out_stride) are not written at all (they keep what the
+ * caller left there). Nothing is written outside the out_capacity slots,
+ * out_lengths[0 .. out_capacity) and out_first[0 .. n].
  *
  * The library keeps a device workspace per (device, stream), made or grown
  * on a call that needs more room; calls on one stream run in order, calls
@@ -584,7 +592,11 @@ int tulips_csum_generate_frames_host(tulips_csum_ctx* ctx, uint8_t* base,
  * tulips_csum_segment_frames with host arrays: out_base (host) receives
  * segment j at out_base + j * out_stride for j < out_capacity, out_lengths
  * (host) its length, out_first (host, n + 1 entries) the exclusive prefix of
- * the per-frame segment counts. Blocks until the outputs are written. */
+ * the per-frame segment counts. Blocks until the outputs are written.
+ * The slots travel back whole, one copy per staging chunk: every slot
+ * j < min(total, out_capacity) is written to its full out_stride, the
+ * segment followed by zeros (a segment longer than out_stride: all zeros,
+ * length 0); no other slot and no other out_lengths entry is touched. */
 int tulips_csum_segment_frames_host(tulips_csum_ctx* ctx, const uint8_t* in_base,
                                     const uint64_t* in_offsets,
                                     const uint16_t* in_lengths, uint32_t n,

@@ -1158,6 +1158,13 @@ segment_host(tulips_csum_ctx* ctx, const uint8_t* in_base, const uint64_t* in_of
         return status_of(e);
       }
       ctx->seg_lens_n = have_lens / 2;
+      // the slots travel back whole (one copy per chunk), and the kernel
+      // writes only the segments' own 16-byte chunks: zero the rest, so the
+      // caller's slot tails never receive what an earlier call left here
+      if ((e = hipMemsetAsync(ctx->d_seg_out, 0, uint64_t(room) * out_stride, st)) !=
+          hipSuccess) {
+        return status_of(e);
+      }
       if ((e = hipMemcpyAsync(s.d_bytes, s.h_bytes, bytes, hipMemcpyHostToDevice, st)) !=
             hipSuccess ||
           (e = hipMemcpyAsync(s.d_offs, s.h_offs, size_t(cnt) * 8, hipMemcpyHostToDevice,

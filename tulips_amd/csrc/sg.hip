@@ -403,10 +403,11 @@ tulips_csum_batch_sg_cpu(const uint8_t* base, const uint64_t* frag_offsets,
                          const uint32_t* src, const uint32_t* dst, uint16_t* out,
                          uint32_t* bad_count, uint32_t n, uint32_t mode)
 {
-  if (bad_count) {
-    *bad_count = 0;
-  }
+  // (a rejected call writes nothing: bad_count is stored only on success)
   if (n == 0) {
+    if (bad_count) {
+      *bad_count = 0;
+    }
     return TULIPS_STATUS_OK;
   }
   if (!seg_first || (!out && !bad_count) || !sg_mode_ok(mode, src, dst) ||
